@@ -16,8 +16,10 @@ GPU.  Strong scaling: `--streams-total T` fixes the job's stream count over G GP
 torchrun the rank comes from RANK / LOCAL_RANK / WORLD_SIZE; `--gpus N` without WORLD_SIZE
 starts the N rank processes itself before anything touches the GPU.
 
-Prints ONE JSON line on rank 0 with the roofline of the dominant kernel (HIP events on the
-pipeline stream), the PCIe-upload-included rate, and the CPU oracle baseline (rank 0, N=1).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and
+prints the line (value, ms_per_step); `--dump-outputs DIR` also writes what the last timed step
+computed as DIR/<name>.npy.  `--full` adds the roofline of the dominant kernel (HIP events on
+the pipeline stream), the PCIe-upload-included rate, and the CPU oracle baseline (rank 0, N=1).
 `--dropin` measures the per-frame drop-in path instead (tools/orbx_dropin.cpp: host threads
 calling orbx_extract / orbx_vocabulary_transform / orbx_search_* one frame at a time).
 """
@@ -792,6 +794,8 @@ def run_marker(args, cfg, rank, world, local, streams, dist):
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_marker_outputs(args.dump_outputs, streams, pipes, B, len(target_desc))
     stages, kernels = {}, {}
     pipe = pipes[0]
     if not args.no_profile:
@@ -894,8 +898,8 @@ def _d2h(ptr, nbytes):
     import ctypes
     hip = ctypes.CDLL("libamdhip64.so")
     out = np.zeros(nbytes, np.uint8)
-    rc = hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr),
-                       ctypes.c_size_t(nbytes), 2)
+    rc = hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(int(ptr)),
+                       ctypes.c_size_t(int(nbytes)), 2)
     if rc != 0:
         raise RuntimeError(f"hipMemcpy D2H failed ({rc})")
     return out
@@ -933,6 +937,98 @@ def dump_verify_frames(out_dir, rank, stream_id, pipe, batch, B, stereo):
         d["depth"] = _d2h(so["depth"], B * cap * 4).view(np.float32).reshape(B, cap)[ids]
     os.makedirs(out_dir, exist_ok=True)
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), **d)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: sampled per-feature arrays of a job (limit 64 MB)
+DUMP_SAMPLE_SEED = 2015
+
+
+def dump_sample(B, n_streams, bytes_per_frame, most=8):
+    """--dump-outputs: the frames of a batch whose per-feature arrays are written — a fixed
+    choice of at most `most` of the B frames (frame 0, which is matched against frame B - 1, then
+    B - 1, then a seeded draw), fewer where the job's camera streams would exceed the byte
+    budget."""
+    n = int(max(1, min(B, most, DUMP_BUDGET_BYTES // max(1, n_streams * bytes_per_frame))))
+    order = np.concatenate([[0, B - 1], np.random.default_rng(DUMP_SAMPLE_SEED).permutation(B)])
+    _, first = np.unique(order, return_index=True)
+    return np.sort(order[np.sort(first)][:n])
+
+
+def dump_frame_outputs(out_dir, stream_ids, pipes, B, stereo, n_streams):
+    """--dump-outputs: what the last timed step left in every camera stream's pipeline, the arrays
+    a caller of FramePipeline reads back, as out_dir/s<stream>_<name>.npy.  `counts` holds the
+    keypoint, SearchByBoW and SearchForTriangulation counts of all B frames (f64 [3][B]); the
+    per-feature arrays hold the frames of `frames` (dump_sample): keypoints (f32 [n][images][cap][7],
+    KEYPOINT_DTYPE's fields) and descriptors (f32 [n][images][cap][32]) of the frame's image(s),
+    node / word id per feature, BowVector (words, values), SearchByBoW match per feature,
+    SearchForTriangulation pairs and, for stereo, mvuRight / mvDepth (f64, the stereo floats f32).
+    Entries past a frame's count are written as 0, whatever the buffers hold there."""
+    from numpy.lib.recfunctions import structured_to_unstructured
+    from ar_orbslam2_amd import KEYPOINT_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    ipf = 2 if stereo else 1
+    for sid, pipe in zip(stream_ids, pipes):
+        pipe.sync()
+        cap = pipe.kp_cap
+        which = dump_sample(B, n_streams, cap * (ipf * (7 + 32) * 4 + 7 * 8 + (8 if stereo else 0)))
+        counts, bow, tri, _ = pipe.results(B)
+        out, bo = pipe.device_outputs(), pipe.bow_outputs()
+        so = pipe.stereo_outputs() if stereo else None
+        img_counts = _d2h(out["counts"], ipf * B * 4).view(np.int32)
+        bow_n = _d2h(bo["bow_n"], B * 4).view(np.int32)
+
+        def rows(ptr, first, item, dtype, n_valid):
+            """Rows first.. of a [.][cap] device array, one per entry of n_valid, as
+            [rows][cap][fields] with the entries past a row's n_valid set to 0."""
+            n = len(n_valid)
+            a = _d2h(ptr + first * cap * item, n * cap * item).view(dtype).reshape(n, cap, -1)
+            for j, nv in enumerate(n_valid):
+                a[j, max(0, int(nv)):] = 0
+            return a
+
+        d = {}
+        for f in which:
+            k = [counts[f]]
+            ki = img_counts[ipf * f:ipf * f + ipf]
+            kp = rows(out["kps"], ipf * f, 28, np.uint8, ki).reshape(-1).view(KEYPOINT_DTYPE)
+            per = {"kps": structured_to_unstructured(kp, dtype=np.float32).reshape(ipf, cap, 7),
+                   "desc": rows(out["desc"], ipf * f, 32, np.uint8, ki).astype(np.float32),
+                   "node_of": rows(out["node_of"], f, 4, np.uint32, k)[0, :, 0].astype(np.float64),
+                   "word_of": rows(bo["word_of"], f, 4, np.uint32, k)[0, :, 0].astype(np.float64),
+                   "bow_words": rows(bo["bow_words"], f, 4, np.uint32, [bow_n[f]])[0, :, 0].astype(np.float64),
+                   "bow_values": rows(bo["bow_values"], f, 8, np.float64, [bow_n[f]])[0, :, 0],
+                   "bow_match": rows(out["bow_match"], f, 4, np.int32, k)[0, :, 0].astype(np.float64),
+                   "tri_pairs": rows(out["tri_pairs"], f, 8, np.int32, [tri[f]])[0].astype(np.float64)}
+            if stereo:
+                per["uright"] = rows(so["uright"], f, 4, np.float32, k)[0, :, 0]
+                per["depth"] = rows(so["depth"], f, 4, np.float32, k)[0, :, 0]
+            for name, v in per.items():
+                d.setdefault(name, []).append(v)
+        d = {k: np.stack(v) for k, v in d.items()}
+        d["frames"] = which.astype(np.float64)
+        d["counts"] = np.stack([counts, bow, tri]).astype(np.float64)
+        d["bow_n"] = bow_n.astype(np.float64)
+        for k, v in d.items():
+            np.save(os.path.join(out_dir, f"s{sid}_{k}.npy"), v)
+
+
+def dump_marker_outputs(out_dir, stream_ids, pipes, B, n_target):
+    """--dump-outputs of the marker path: per camera stream the keypoint and good-match counts of
+    all B frames of the last timed step (f64 [2][B]), the BruteForceMatcher matches (f32
+    [B][n_target][4]: DMATCH_DTYPE's fields) and Marker::Match's good flags (f32 [B][n_target])."""
+    from numpy.lib.recfunctions import structured_to_unstructured
+    from ar_orbslam2_amd import _ffi
+    os.makedirs(out_dir, exist_ok=True)
+    for sid, pipe in zip(stream_ids, pipes):
+        pipe.sync()
+        kp, good = pipe.results(B)
+        out = pipe.device_outputs()
+        m = _d2h(out["matches"], B * n_target * 16).view(_ffi.DMATCH_DTYPE)
+        np.save(os.path.join(out_dir, f"s{sid}_counts.npy"), np.stack([kp, good]).astype(np.float64))
+        np.save(os.path.join(out_dir, f"s{sid}_matches.npy"),
+                structured_to_unstructured(m, dtype=np.float32).reshape(B, n_target, 4))
+        np.save(os.path.join(out_dir, f"s{sid}_good.npy"),
+                _d2h(out["good"], B * n_target).astype(np.float32).reshape(B, n_target))
 
 
 def replay_step(pipes, pools, B, i):
@@ -984,8 +1080,11 @@ def run_frames(args, cfg, rank, world, local, streams, dist):
     if args.verify_frames:
         dump_verify_frames(args.verify_frames, rank, streams[0], pipes[0],
                            pools[0][(args.steps - 1) % len(pools[0])], B, bool(stereo))
-    # roofline pass (after timing): stream 0 alone with HIP events around every kernel on the
-    # stream it launches on, so a kernel's event interval is its own duration (as rocprofv3
+    if args.dump_outputs:
+        dump_frame_outputs(args.dump_outputs, streams, pipes, B, bool(stereo),
+                           args.streams_total or world * max(1, args.streams))
+    # roofline pass (--full, after timing): stream 0 alone with HIP events around every kernel on
+    # the stream it launches on, so a kernel's event interval is its own duration (as rocprofv3
     # reports it) rather than a share of the concurrent streams
     stages, kernels = {}, {}
     if not args.no_profile:
@@ -1133,8 +1232,17 @@ def parse_args(argv=None):
                          "(with --dist-backend gloo; RCCL refuses two ranks on one GPU)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher + sharding + aggregation only, no device work (gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the CPU oracle baseline, the per-kernel roofline "
+                         "pass and the PCIe-upload-included rate (each with its own switch below); "
+                         "a run without --full sets up, warms up, times the steps and prints the "
+                         "result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (every camera "
+                         "stream's counts; keypoints, descriptors, BoW, matches of a fixed seeded "
+                         "sample of its frames) to DIR/<name>.npy as float32 / float64")
     ap.add_argument("--upload", dest="upload", action="store_true", default=True,
-                    help="also measure the rate with frames uploaded from pinned host memory")
+                    help="--full: also measure the rate with frames uploaded from pinned host memory")
     ap.add_argument("--no-upload", dest="upload", action="store_false")
     ap.add_argument("--dropin", action="store_true",
                     help="measure the drop-in per-frame path (host images, one frame per call)")
@@ -1164,6 +1272,8 @@ def parse_args(argv=None):
     ap.add_argument("--roofline-steps", type=int, default=5,
                     help="steps of the single-stream roofline pass (per-kernel HIP events)")
     args = ap.parse_args(argv)
+    if not args.full:  # the plain run: only what the headline figure needs
+        args.no_cpu_baseline, args.no_profile, args.upload = True, True, False
     if args.batch is None:
         args.batch = CONFIGS[args.config].get("batch", 256)
     if args.pmc_dir is None:  # this round's committed PMC passes of the config's default command

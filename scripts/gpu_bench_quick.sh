@@ -5,7 +5,7 @@ set -o pipefail
 T=${1:-bq}
 mkdir -p gpurun_out/$T
 for C in ${2:-C2}; do
-  timeout -k 10 300 python bench.py --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload \
+  timeout -k 10 300 python bench.py --full --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload \
     > gpurun_out/$T/$C.jsonl 2> gpurun_out/$T/$C.err || exit 2
 done
 python - <<PY

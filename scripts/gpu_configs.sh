@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest ${2:-tests} -m gpu -q -x --timeout 300 --t
   > gpurun_out/$T/tests.txt 2>&1 || { tail -30 gpurun_out/$T/tests.txt; exit 1; }
 tail -1 gpurun_out/$T/tests.txt
 for C in C2 C3 C4 C5 AR; do
-  timeout -k 10 200 python bench.py --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload \
+  timeout -k 10 200 python bench.py --full --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload \
     > gpurun_out/$T/$C.jsonl 2> gpurun_out/$T/$C.err || { tail -5 gpurun_out/$T/$C.err; exit 2; }
   python - gpurun_out/$T/$C.jsonl $C <<'PY'
 import json, sys

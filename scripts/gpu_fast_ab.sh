@@ -13,7 +13,7 @@ for round in 1 2; do
   for v in default $2; do
     for C in ${3:-C2 C5}; do
       if [ $v = default ]; then env=""; else env="ORBX_LIB_DIR=ar_orbslam2_amd/_lib_exp/$v ORBX_ALLOW_CUSTOM_BUILD=1"; fi
-      env $env timeout -k 10 300 python bench.py --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload \
+      env $env timeout -k 10 300 python bench.py --full --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload \
         > gpurun_out/$T/${v}_$C.$round.jsonl 2> gpurun_out/$T/${v}_$C.$round.err || { tail -5 gpurun_out/$T/${v}_$C.$round.err; exit 2; }
       python - gpurun_out/$T/${v}_$C.$round.jsonl $v $C <<'PY'
 import json, sys

@@ -8,13 +8,13 @@ O=$R/gpurun_out/$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- \
-  python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-upload ${2:-} > $O/bench.jsonl 2> $O/trace.err || exit 1
+  python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-upload ${2:-} > $O/bench.jsonl 2> $O/trace.err || exit 1
 cp $(find $O/trace -name "*kernel_stats.csv") $O/kernel_stats.csv
 cp $(find $O/trace -name "*kernel_trace.csv") $O/kernel_trace.csv
 rm -rf $O/trace
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VALU2 SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS"
 timeout -s KILL 150 rocprofv3 --pmc $SQ --output-format csv -d $O/s -o run -- \
-  python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-upload ${2:-} > /dev/null 2> $O/s.err || exit 2
+  python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-upload ${2:-} > /dev/null 2> $O/s.err || exit 2
 cp $(find $O/s -name "*counter_collection.csv") $O/sq.csv
 rm -rf $O/s
 python3 $R/scripts/pmc_compact.py $O > /dev/null 2>&1 || true

@@ -12,7 +12,7 @@ for round in 1 2; do
   for v in default $2; do
     if [ $v = default ]; then env=""; else env="ORBX_LIB_DIR=ar_orbslam2_amd/_lib_exp/$v ORBX_ALLOW_CUSTOM_BUILD=1"; fi
     for C in C2 C5; do
-      env $env timeout -k 10 300 python bench.py --config $C --steps 10 --warmup 2 --no-cpu-baseline --no-upload \
+      env $env timeout -k 10 300 python bench.py --full --config $C --steps 10 --warmup 2 --no-cpu-baseline --no-upload \
         > gpurun_out/$T/${v}_$C.$round.jsonl 2> gpurun_out/$T/${v}_$C.$round.err || { tail -5 gpurun_out/$T/${v}_$C.$round.err; exit 2; }
     done
     env $env timeout -k 10 200 python bench.py --dropin --threads 1 --dropin-frames 400 > gpurun_out/$T/${v}_d1.$round.json 2> gpurun_out/$T/${v}_d1.$round.err || exit 4

@@ -10,7 +10,7 @@ case "${ORBX_LIB_DIR:-}" in ""|/*) ;; *) export ORBX_LIB_DIR=$R/$ORBX_LIB_DIR ;;
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 150 rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCC_HIT_sum TCC_MISS_sum \
-  --output-format csv -d $O/p -o run -- python3 $R/bench.py --no-cpu-baseline --no-upload --steps 5 "$@" > $O/b.json 2> $O/p.err || { tail -5 $O/p.err; exit 1; }
+  --output-format csv -d $O/p -o run -- python3 $R/bench.py --full --no-cpu-baseline --no-upload --steps 5 "$@" > $O/b.json 2> $O/p.err || { tail -5 $O/p.err; exit 1; }
 cp $(find $O/p -name "*counter_collection.csv") $O/tcp.csv && rm -rf $O/p
 python3 - $O/tcp.csv <<'PY'
 import csv, sys, collections

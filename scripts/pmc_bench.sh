@@ -10,11 +10,11 @@ SQ="SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VALU2 SQ_INSTS_SAL
 mkdir -p $D
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/f -o run -- \
-  python3 $R/bench.py --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/f.err
+  python3 $R/bench.py --full --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/f.err
 timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/w -o run -- \
-  python3 $R/bench.py --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/w.err
+  python3 $R/bench.py --full --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/w.err
 timeout -s KILL 150 rocprofv3 --pmc $SQ --output-format csv -d $D/s -o run -- \
-  python3 $R/bench.py --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/s.err
+  python3 $R/bench.py --full --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/s.err
 cp $(find $D/f -name "*counter_collection.csv") $D/fetch_size.csv
 cp $(find $D/w -name "*counter_collection.csv") $D/write_size.csv
 cp $(find $D/s -name "*counter_collection.csv") $D/sq_counters.csv

@@ -10,6 +10,6 @@ SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_
 mkdir -p $D
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 150 rocprofv3 --pmc $SQ --output-format csv -d $D/s -o run -- \
-  python3 $R/bench.py --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/s.err
+  python3 $R/bench.py --full --no-cpu-baseline --no-upload --steps 5 "$@" > /dev/null 2> $D/s.err
 cp $(find $D/s -name "*counter_collection.csv") $D/stall.csv
 rm -rf $D/s

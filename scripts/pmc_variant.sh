@@ -11,18 +11,18 @@ if [ "$V" != default ]; then export ORBX_LIB_DIR=$R/ar_orbslam2_amd/_lib_exp/$V 
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VALU2 SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS"
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc $SQ --output-format csv -d $D/s -o run -- \
-  python3 $R/bench.py --config $C --no-cpu-baseline --no-upload --steps 5 > /dev/null 2> $D/s.err
+  python3 $R/bench.py --full --config $C --no-cpu-baseline --no-upload --steps 5 > /dev/null 2> $D/s.err
 cp $(find $D/s -name "*counter_collection.csv") $D/sq_counters.csv
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/f -o run -- \
-  python3 $R/bench.py --config $C --no-cpu-baseline --no-upload --steps 5 > /dev/null 2> $D/f.err
+  python3 $R/bench.py --full --config $C --no-cpu-baseline --no-upload --steps 5 > /dev/null 2> $D/f.err
 cp $(find $D/f -name "*counter_collection.csv") $D/fetch_size.csv
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/w -o run -- \
-  python3 $R/bench.py --config $C --no-cpu-baseline --no-upload --steps 5 > /dev/null 2> $D/w.err
+  python3 $R/bench.py --full --config $C --no-cpu-baseline --no-upload --steps 5 > /dev/null 2> $D/w.err
 cp $(find $D/w -name "*counter_collection.csv") $D/write_size.csv
 rm -rf $D/s $D/f $D/w
 python3 $R/scripts/pmc_compact.py $D
 cd $R
-timeout -k 10 200 python bench.py --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload --pmc-dir $D > $D/bench.jsonl 2> $D/bench.err
+timeout -k 10 200 python bench.py --full --config $C --steps 20 --warmup 3 --no-cpu-baseline --no-upload --pmc-dir $D > $D/bench.jsonl 2> $D/bench.err
 python3 - $D <<'PY'
 import csv, json, sys
 D = sys.argv[1]

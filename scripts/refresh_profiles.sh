@@ -28,21 +28,21 @@ if [ "$PART" = configs ]; then
     c=$(echo $C | tr A-Z a-z)
     (cd /tmp && export TMPDIR=/tmp && D=$O/${TAG}_pmc_$c && mkdir -p $D &&
      timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/f -o run -- \
-       python3 $R/bench.py --config $C --no-cpu-baseline --steps 5 > /dev/null 2> $D/f.err &&
+       python3 $R/bench.py --full --config $C --no-cpu-baseline --steps 5 > /dev/null 2> $D/f.err &&
      timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/w -o run -- \
-       python3 $R/bench.py --config $C --no-cpu-baseline --steps 5 > /dev/null 2> $D/w.err &&
+       python3 $R/bench.py --full --config $C --no-cpu-baseline --steps 5 > /dev/null 2> $D/w.err &&
      timeout -s KILL 150 rocprofv3 --pmc $SQ --output-format csv -d $D/s -o run -- \
-       python3 $R/bench.py --config $C --no-cpu-baseline --steps 5 > /dev/null 2> $D/s.err &&
+       python3 $R/bench.py --full --config $C --no-cpu-baseline --steps 5 > /dev/null 2> $D/s.err &&
      cp $(find $D/f -name "*counter_collection.csv") $D/fetch_size.csv &&
      cp $(find $D/w -name "*counter_collection.csv") $D/write_size.csv &&
      cp $(find $D/s -name "*counter_collection.csv") $D/sq_counters.csv && rm -rf $D/f $D/w $D/s &&
      python3 $R/scripts/pmc_compact.py $D)
-    timeout -k 10 300 python -u bench.py --config $C --pmc-dir $O/${TAG}_pmc_$c \
+    timeout -k 10 300 python -u bench.py --full --config $C --pmc-dir $O/${TAG}_pmc_$c \
       > $O/${TAG}_bench_$c.jsonl 2> $O/bench_$c.err
     cat $O/${TAG}_bench_$c.jsonl
     (cd /tmp && export TMPDIR=/tmp &&
      timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$c -o run -- \
-       python3 $R/bench.py --config $C --no-cpu-baseline --pmc-dir $O/${TAG}_pmc_$c \
+       python3 $R/bench.py --full --config $C --no-cpu-baseline --pmc-dir $O/${TAG}_pmc_$c \
        > $O/${TAG}_bench_${c}_under_rocprof.jsonl 2> $O/trace_$c.err &&
      cp $(find $O/trace_$c -name "*kernel_stats.csv") $O/${TAG}_kernel_stats_$c.csv &&
      mkdir -p $O/traces && cp $(find $O/trace_$c -name "*kernel_trace.csv") $O/traces/kernel_trace_$c.csv &&
@@ -60,11 +60,11 @@ pmc() {  # pmc <outdir> <bench args...>
   local D=$1; shift
   mkdir -p $D
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/f -o run -- \
-    python3 $R/bench.py --no-cpu-baseline --steps 5 "$@" > /dev/null 2> $D/f.err
+    python3 $R/bench.py --full --no-cpu-baseline --steps 5 "$@" > /dev/null 2> $D/f.err
   timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/w -o run -- \
-    python3 $R/bench.py --no-cpu-baseline --steps 5 "$@" > /dev/null 2> $D/w.err
+    python3 $R/bench.py --full --no-cpu-baseline --steps 5 "$@" > /dev/null 2> $D/w.err
   timeout -s KILL 120 rocprofv3 --pmc $SQ --output-format csv -d $D/s -o run -- \
-    python3 $R/bench.py --no-cpu-baseline --steps 5 "$@" > /dev/null 2> $D/s.err
+    python3 $R/bench.py --full --no-cpu-baseline --steps 5 "$@" > /dev/null 2> $D/s.err
   cp $(find $D/f -name "*counter_collection.csv") $D/fetch_size.csv
   cp $(find $D/w -name "*counter_collection.csv") $D/write_size.csv
   cp $(find $D/s -name "*counter_collection.csv") $D/sq_counters.csv
@@ -74,17 +74,17 @@ pmc() {  # pmc <outdir> <bench args...>
 pmc $O/${TAG}_pmc
 pmc $O/${TAG}_pmc_ar --config AR
 cd $R
-timeout -k 10 300 python -u bench.py --pmc-dir $O/${TAG}_pmc > $O/${TAG}_bench.jsonl 2> $O/bench.err
+timeout -k 10 300 python -u bench.py --full --pmc-dir $O/${TAG}_pmc > $O/${TAG}_bench.jsonl 2> $O/bench.err
 cat $O/${TAG}_bench.jsonl
-timeout -k 10 300 python -u bench.py --config AR --pmc-dir $O/${TAG}_pmc_ar \
+timeout -k 10 300 python -u bench.py --full --config AR --pmc-dir $O/${TAG}_pmc_ar \
   > $O/${TAG}_bench_ar.jsonl 2> $O/bench_ar.err
 cat $O/${TAG}_bench_ar.jsonl
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- \
-  python3 $R/bench.py --no-cpu-baseline --pmc-dir $O/${TAG}_pmc > $O/${TAG}_bench_under_rocprof.jsonl 2> $O/trace.err
+  python3 $R/bench.py --full --no-cpu-baseline --pmc-dir $O/${TAG}_pmc > $O/${TAG}_bench_under_rocprof.jsonl 2> $O/trace.err
 cp $(find $O/trace -name "*kernel_stats.csv") $O/${TAG}_kernel_stats.csv
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_ar -o run -- \
-  python3 $R/bench.py --config AR --no-cpu-baseline --pmc-dir $O/${TAG}_pmc_ar \
+  python3 $R/bench.py --full --config AR --no-cpu-baseline --pmc-dir $O/${TAG}_pmc_ar \
   > $O/${TAG}_bench_ar_under_rocprof.jsonl 2> $O/trace_ar.err
 cp $(find $O/trace_ar -name "*kernel_stats.csv") $O/${TAG}_kernel_stats_ar.csv
 mkdir -p $O/traces

@@ -76,10 +76,11 @@ def check_verify_dump(path, nf, stereo_cfg=None):
 def test_two_ranks_same_device(extra, streams, tmp_path):
     """Two real ranks; besides the counts, rank 0's and rank 1's own outputs (frames {0, B-1} of
     their first camera stream, --verify-frames) equal the oracle."""
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
            "--dist-backend", "gloo", "--same-device", "--steps", "3", "--warmup", "1",
            "--batch", "32", "--pool", "2", "--streams", "2", "--no-cpu-baseline", "--no-upload",
-           "--roofline-steps", "1", "--verify-frames", str(tmp_path)] + extra
+           "--roofline-steps", "1", "--verify-frames", str(tmp_path),
+           "--dump-outputs", str(tmp_path / "dump")] + extra
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -98,6 +99,53 @@ def test_two_ranks_same_device(extra, streams, tmp_path):
     assert out["scaling"] == ("strong" if extra else "weak")
     for r in (0, 1):
         assert check_verify_dump(os.path.join(tmp_path, f"rank{r}.npz"), 1000) == streams[r][0]
+        check_output_dump(tmp_path / "dump", streams[r], os.path.join(tmp_path, f"rank{r}.npz"))
+    files = os.listdir(tmp_path / "dump")
+    assert len(files) == 11 * n and sum(os.path.getsize(tmp_path / "dump" / f) for f in files) < 64e6
+
+
+def check_output_dump(dump, stream_ids, verify_path):
+    """--dump-outputs of one rank: f32 / f64 arrays per camera stream, the seeded frame sample;
+    the first stream's dump agrees with the rank's oracle-checked --verify-frames dump (same
+    step): every count, and keypoints, descriptors, matches and pairs of the frames both hold."""
+    import bench
+    v = np.load(verify_path)
+    B = int(v["batch"])
+    for i, sid in enumerate(stream_ids):
+        d = {k: np.load(dump / f"s{sid}_{k}.npy") for k in
+             ("frames", "counts", "bow_n", "kps", "desc", "node_of", "word_of", "bow_words",
+              "bow_values", "bow_match", "tri_pairs")}
+        assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+        which = d["frames"].astype(int)
+        assert np.array_equal(which, bench.dump_sample(B, 4, 1))  # tiny frames: the full sample
+        assert which[0] == 0 and which[-1] == B - 1
+        cap = d["kps"].shape[2]
+        assert d["kps"].shape == (len(which), 1, cap, 7) and d["desc"].shape == (len(which), 1, cap, 32)
+        assert d["counts"].shape == (3, B) and (d["counts"][0] > 0).all()
+        for j, f in enumerate(which):
+            k = int(d["counts"][0, f])
+            assert not d["desc"][j, 0, k:].any() and not d["kps"][j, 0, k:].any()
+            assert d["desc"][j, 0, :k].any() and not d["node_of"][j, k:].any()
+            nt = int(d["counts"][2, f])
+            assert (d["tri_pairs"][j, :nt] >= 0).all() and not d["tri_pairs"][j, nt:].any()
+        if i:
+            continue
+        ids = [int(x) for x in v["frame_ids"]]
+        assert np.array_equal(d["counts"][0, ids], v["counts"])
+        assert np.array_equal(d["counts"][1, [0, B - 1]], v["bow"])
+        assert np.array_equal(d["counts"][2, [0, B - 1]], v["tri"])
+        for j, f in enumerate(which):
+            if f not in (0, B - 1):
+                continue
+            vi, vm = ids.index(f), [0, B - 1].index(f)
+            k = int(v["counts"][vi])
+            from numpy.lib.recfunctions import structured_to_unstructured
+            assert np.array_equal(d["kps"][j, 0, :k],
+                                  structured_to_unstructured(v["kps"][vi][:k], dtype=np.float32))
+            assert np.array_equal(d["desc"][j, 0, :k], v["desc"][vi][:k])
+            assert np.array_equal(d["bow_match"][j, :k], v["match"][vm][:k])
+            nt = int(v["tri"][vm])
+            assert np.array_equal(d["tri_pairs"][j, :nt], v["pairs"][vm][:nt])
 
 
 @pytest.mark.timeout(600)
@@ -105,7 +153,7 @@ def test_two_ranks_same_device_stereo(tmp_path):
     """The N > 1 path on a stereo config (C3, EuRoC geometry): rank 1's frames — both images,
     mvuRight / mvDepth and both matchers — equal the oracle."""
     import bench
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--config", "C3", "--gpus", "2",
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--config", "C3", "--gpus", "2",
            "--dist-backend", "gloo", "--same-device", "--steps", "2", "--warmup", "1",
            "--batch", "16", "--pool", "2", "--streams", "1", "--no-cpu-baseline", "--no-upload",
            "--roofline-steps", "1", "--verify-frames", str(tmp_path)]

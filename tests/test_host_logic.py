@@ -335,3 +335,36 @@ def test_roofline_bytes_follow_survey_8d():
     b = r["builder_model"]
     assert b["algorithmic_bytes_per_launch"] == pytest.approx(r["algorithmic_bytes_per_launch"] + 307200 / 3)
     assert b["frac"] > r["frac"]
+
+
+def test_bench_plain_run_leaves_the_extra_measurements_to_full():
+    """A plain bench run does only what the headline figure needs: the CPU baseline, the roofline
+    pass and the PCIe-included rate run under --full, where their own switches still apply."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu_baseline and a.no_profile and not a.upload
+    a = bench.parse_args(["--full"])
+    assert not a.no_cpu_baseline and not a.no_profile and a.upload
+    a = bench.parse_args(["--full", "--no-upload", "--no-profile", "--dump-outputs", "d"])
+    assert not a.no_cpu_baseline and a.no_profile and not a.upload and a.dump_outputs == "d"
+
+
+def test_bench_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs writes the per-feature arrays of the same seeded frames in every run, and
+    of fewer frames where the job's camera streams would exceed the byte budget."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    s = bench.dump_sample(512, 3, 1 << 20)
+    assert np.array_equal(s, bench.dump_sample(512, 3, 1 << 20))
+    assert len(s) == 8 and len(set(s)) == 8 and np.array_equal(s, np.sort(s))
+    assert 0 <= s.min() and s.max() < 512
+    assert np.array_equal(bench.dump_sample(4, 1, 1), np.arange(4))
+    big = bench.dump_sample(256, 8, 2 << 20)  # 8 streams x 2 MiB per frame: 3 frames fit
+    assert len(big) == 3 and 8 * len(big) * (2 << 20) <= bench.DUMP_BUDGET_BYTES
+    assert len(bench.dump_sample(256, 64, 2 << 20)) == 1
