@@ -33,7 +33,7 @@
 
 namespace orbx {
 
-__constant__ int8_t c_pattern[1024];
+__constant__ __align__(16) int8_t c_pattern[1024];
 __constant__ int c_umax[kHalfPatch + 1];
 __constant__ IcMask c_icmask;                   // IC_Angle row masks from umax
 
@@ -2092,17 +2092,31 @@ void k_octree(
 // unblurred level (ORBextractor.cc:73-98), cv::fastAtan2, glibc sincosf, rBRIEF on the blurred
 // level with the reference binary's fmaf + cvRound sampling (ORBextractor.cc:101-144, SURVEY
 // A.6) — lane j produces descriptor byte j from pairs 8j..8j+7 — then the level-0 scaling of
-// operator() (:1035-1041).  Output is level-major like `_keypoints`/`descriptors`.  Two
-// keypoints per wave share the per-keypoint scalar work (angle, sincos, addressing).
+// operator() (:1035-1041).  Output is level-major like `_keypoints`/`descriptors`.
+//
+// A workgroup takes a tile of kDescTile consecutive slots in three phases, so the per-keypoint
+// math runs one keypoint per lane and not once per half-wave:
+//   A  kDescTile / kDescKP rounds: half-wave hw stages the raw patch of slot 8 r + hw and leaves
+//      its moments (m10, m01) in LDS;
+//   B  wave 0, lane = slot: angle, sincos, output position and the keypoint record;
+//   C  the same rounds on the blurred patch: rBRIEF with the slot's (sin, cos) from LDS.
+// Every wave holds the tile's 64 (key, level geometry) values, one slot per lane, and a round
+// takes its slot's by __shfl.  In A and C the next round's patch loads are issued before the
+// current round's arithmetic.
 struct KpOffsets {  // per-level first keypoint slot (LevelGeom::kp_off), by value
   int off[kMaxLevels + 1];
 };
 
-// keypoints (half-waves) per workgroup (16 / 32 measured 8 % / 45 % slower at C2)
+// patches in flight (half-waves) per workgroup (16 / 32 measured 8 % / 45 % slower at C2)
 constexpr int kDescKP = 8;
+// keypoint slots per workgroup: one per lane of a wave
+constexpr int kDescTile = 64;
+// waves per SIMD the registers must allow: what the 26 KB of LDS per workgroup allows
+constexpr int kDescWaves = 6;
 
 template <class K>
-__global__ __launch_bounds__(32 * kDescKP) void k_describe(
+__global__ __launch_bounds__(32 * kDescKP) __attribute__((amdgpu_waves_per_eu(kDescWaves)))
+void k_describe(
     const uint8_t* __restrict__ pyr, int64_t pyr_bytes, const uint8_t* __restrict__ blur,
     const LevelGeom* __restrict__ lv, int nlevels, KpOffsets ko, const K* __restrict__ okey,
     const int* __restrict__ oidx, const int* __restrict__ ocount, int kp_total,
@@ -2113,124 +2127,224 @@ __global__ __launch_bounds__(32 * kDescKP) void k_describe(
   // different rows spread over the LDS banks
   constexpr int RW = 10, BW = 13, BC = 4;  // BC: 16-B pieces per blurred row
   constexpr int RN = 31 * RW, BN = 37 * BW;
+  constexpr int NR = kDescTile / kDescKP;  // rounds per phase
+  constexpr int RK = 11, BK = 5;           // loads per lane and round: raw dwords, blurred pieces
+  static_assert(kDescTile == 64 && kDescKP == 8, "one slot per lane, two half-waves per wave");
   __shared__ uint32_t s_raw[kDescKP][RN];
   __shared__ uint32_t s_blr[kDescKP][BN];
+  __shared__ uint2 s_kp[kDescTile];  // phase A: (m10, m01); from phase B on: (sin, cos)
+  __shared__ int s_out[kDescTile];   // output position
   int bx, img;
   xcd_block(bx, img);
   const int lane = threadIdx.x & 63, hl = lane & 31;
   const int hw = threadIdx.x >> 5;  // half-wave of the workgroup, 0..7
-  const int slot = bx * kDescKP + hw;
   const int* oc = ocount + img * nlevels;
   if (bx == 0 && threadIdx.x == 0) {
     int t = 0;
     for (int l = 0; l < nlevels; l++) t += oc[l];
     counts[img] = t;
   }
-  int level = 0;
+  // the lane's slot of the tile (the same 64 in every wave): its level, count, key and the
+  // level's fields in one round of loads, pinned in registers.  The level's keys come in
+  // candidate order (spatial neighbours together, k_octree's retain), each with the node-order
+  // position it is written to.
+  const int slot = bx * kDescTile + lane;
+  int level = 0, loff = ko.off[0];
 #pragma unroll
-  for (int l = 1; l < kMaxLevels; l++) level += (l < nlevels && slot >= ko.off[l]);
+  for (int l = 1; l < kMaxLevels; l++)
+    if (l < nlevels && slot >= ko.off[l]) {
+      level = l;
+      loff = ko.off[l];
+    }
   const LevelGeom& G = lv[level];
-  const int idx = slot - ko.off[level];
-  // the count, the key and the level's fields in one round of loads, pinned in registers (a
-  // rematerialised load of G per patch row would serialise the patch loads behind it)
-  // the level's keys come in candidate order (spatial neighbours together, k_octree's retain),
-  // each with the node-order position it is written to
   int noc = oc[level];
   K key = okey[(int64_t)img * kp_total + min(slot, kp_total - 1)];
   int opos = oidx[(int64_t)img * kp_total + min(slot, kp_total - 1)];
   int pitch = G.pitch, pyr_off = (int)G.pyr_off;
-  float lscale = G.scale, lsize = G.size;
-  asm volatile("" : "+v"(noc), "+v"(key), "+v"(opos), "+v"(pitch), "+v"(pyr_off), "+v"(lscale),
-               "+v"(lsize));
-  const bool active = slot < kp_total && idx < noc;  // uniform within the half-wave
+  asm volatile("" : "+v"(noc), "+v"(key), "+v"(opos), "+v"(pitch), "+v"(pyr_off));
+  const bool active = slot < kp_total && slot - loff < noc;
+  const uint64_t amask = __ballot(active);  // the same in every wave
+  if (amask == 0) return;
   if (!active) key = 0;
   const int cx = active ? KeyFmt<K>::x(key) + (kEdge - 3) : 0;
   const int cy = active ? KeyFmt<K>::y(key) + (kEdge - 3) : 0;
-  // stage both patches with aligned dword loads issued together: the raw 31 x 31 patch
-  // (IC_Angle, radius 15) and the blurred 37 x 37 patch (rBRIEF samples, radius <= 18)
-  const uint8_t* L = pyr + (int64_t)img * pyr_bytes + pyr_off;
-  const uint8_t* Bp = blur + (int64_t)img * pyr_bytes + pyr_off;
-  const int fr = (cx - 15) >> 2, lr = (cx + 15) >> 2;  // raw dword columns
-  const int ab = (cx - 18) & ~15, lb = ((cx + 18) & ~15) - ab;  // blurred first piece, last offset
-  if (active) {
-    uint32_t vr[(RN + 31) / 32];
-    uint4 vb[(37 * BC + 31) / 32];
+  // round r of a phase: this half-wave works on slot 8 r + hw of the tile (the eight patches in
+  // flight are spatial neighbours); uniform within the half-wave
+  struct Geo {
+    int cx, cy, pitch, off;
+    bool act;
+  };
+  auto geo = [&](int r) {
+    const int s = kDescKP * r + hw;
+    Geo g;
+    g.cx = __shfl(cx, s);
+    g.cy = __shfl(cy, s);
+    g.pitch = __shfl(pitch, s);
+    g.off = __shfl(pyr_off, s);
+    g.act = (amask >> s) & 1;
+    return g;
+  };
+  const uint8_t* L = pyr + (int64_t)img * pyr_bytes;
+  const uint8_t* Bp = blur + (int64_t)img * pyr_bytes;
+
+  // ---- phase A: the raw 31 x 31 patch (IC_Angle, radius 15) by aligned dwords.  Lane hl < 30
+  // takes dword column rc of rows rr, rr + 3, ..., rr + 27 and of row 30 (kept by rr == 0), so
+  // load k goes to s_raw[30 k + hl].  Columns past the patch's last dword re-read that dword
+  // (never past the patch, and never used: IC_Angle masks those bytes).
+  const int rl = min(hl, 29), rr = rl / RW, rc = rl - rr * RW;
+  auto load_raw = [&](const Geo& g, uint32_t(&v)[RK]) {
+    const int fr = (g.cx - 15) >> 2, lr = (g.cx + 15) >> 2;  // raw dword columns
+    const uint8_t* p = L + (uint32_t)(g.off + (g.cy - 15) * g.pitch + 4 * min(fr + rc, lr));
+    const uint32_t rp = (uint32_t)(rr * g.pitch);
 #pragma unroll
-    for (int k = 0; k < (RN + 31) / 32; k++) {
-      const int i = hl + 32 * k, r = i / RW, c = i - r * RW;
-      vr[k] = (i < RN && fr + c <= lr)
-                  ? *(const uint32_t*)(L + (uint32_t)((cy - 15 + r) * pitch + 4 * (fr + c)))
-                  : 0u;
-    }
+    for (int k = 0; k < RK - 1; k++)
+      v[k] = *(const uint32_t*)(p + (rp + (uint32_t)(3 * k * g.pitch)));
+    v[RK - 1] = *(const uint32_t*)(p + (uint32_t)(30 * g.pitch));
+  };
+  {
+    // the lane's row mask, loaded ahead of the rounds: a load issued after a round's prefetch
+    // would make its use wait for the prefetch as well
+    uint32_t mk[8];
 #pragma unroll
-    for (int k = 0; k < (37 * BC + 31) / 32; k++) {  // 16-B pieces: 5 loads per lane, not 13
-      const int i = hl + 32 * k, r = i >> 2, c = i & 3;
-      vb[k] = (i < 37 * BC && 16 * c <= lb)
-                  ? *(const uint4*)(Bp + (uint32_t)((cy - 18 + r) * pitch + ab + 16 * c))
-                  : make_uint4(0u, 0u, 0u, 0u);
-    }
+    for (int k = 0; k < 8; k++) mk[k] = c_icmask.m[min(hl, 30)][k];
 #pragma unroll
-    for (int k = 0; k < (RN + 31) / 32; k++)
-      if (hl + 32 * k < RN) s_raw[hw][hl + 32 * k] = vr[k];
+    for (int k = 0; k < 8; k++) asm volatile("" : "+v"(mk[k]));
+    Geo g = geo(0);
+    uint32_t vr[RK] = {};
+    if (g.act) load_raw(g, vr);
+#pragma unroll 1
+    for (int r = 0; r < NR; r++) {
+      const Geo c = g;
+      if (c.act && hl < 30) {
 #pragma unroll
-    for (int k = 0; k < (37 * BC + 31) / 32; k++) {
-      const int i = hl + 32 * k, r = i >> 2, c = i & 3;
-      if (i < 37 * BC) {
-        uint32_t* d = s_blr[hw] + r * BW + 4 * c;
-        d[0] = vb[k].x;
-        if (4 * c + 1 < BW) d[1] = vb[k].y;
-        if (4 * c + 2 < BW) d[2] = vb[k].z;
-        if (4 * c + 3 < BW) d[3] = vb[k].w;
+        for (int k = 0; k < RK - 1; k++) s_raw[hw][30 * k + hl] = vr[k];
+        if (hl < RW) s_raw[hw][30 * (RK - 1) + hl] = vr[RK - 1];
       }
+      if (r + 1 < NR) {  // the next round's loads fly during this round's moments
+        g = geo(r + 1);
+        if (g.act) load_raw(g, vr);
+      }
+      wave_sync();
+      // IC_Angle (ORBextractor.cc:73-98): lane hl < 31 sums row v = hl - 15 of the circular
+      // patch (v_dot4_u32_u8 over the row's bytes masked to |u| <= umax[|v|])
+      int m10 = 0, m01 = 0;
+      if (c.act && hl < 31)
+        ic_row_moments(s_raw[hw] + hl * RW, (c.cx - 15) & 3, mk, hl - 15, m10, m01);
+      // sums within the half-wave: 16-lane rows on DPP, then the two rows of the half
+      m10 = row16_sum(m10);
+      m01 = row16_sum(m01);
+      m10 += __shfl_xor(m10, 16);
+      m01 += __shfl_xor(m01, 16);
+      if (c.act && hl == 0) s_kp[kDescKP * r + hw] = make_uint2((uint32_t)m10, (uint32_t)m01);
+      wave_sync();  // the next round's staging overwrites s_raw[hw]
     }
   }
-  constexpr int BS = 4 * BW;
-  const uint8_t* bc = (const uint8_t*)s_blr[hw] + 18 * BS + (cx - ab);
-  // IC_Angle (ORBextractor.cc:73-98): lane hl < 31 sums row v = hl - 15 of the circular patch
-  // (v_dot4_u32_u8 over the row's bytes masked to |u| <= umax[|v|])
-  int m10 = 0, m01 = 0;
-  if (active && hl < 31)
-    ic_row_moments(s_raw[hw] + hl * RW, (cx - 15) - 4 * fr, c_icmask.m[hl], hl - 15, m10, m01);
-  // sums within the half-wave: 16-lane rows on DPP, then the two rows of the half
-  m10 = row16_sum(m10);
-  m01 = row16_sum(m01);
-  m10 += __shfl_xor(m10, 16);
-  m01 += __shfl_xor(m01, 16);
-  if (!active) return;
-  const float angle = orbx_fast_atan2((float)m01, (float)m10);
-  // descriptor on the blurred level: byte hl from pairs 8 hl .. 8 hl + 7, LSB first
-  const float factorPI = (float)(3.14159265358979323846 / 180.f);
-  float sn, cs;
-  orbx_sincosf(angle * factorPI, &sn, &cs);
-  // rotated samples in packed f32 with the reference's fmaf pattern, rounded by the magic
-  // addend; the (row, col) -> byte offset bias is folded into the centre address
-  const uint8_t* bcb = bc - sample_bias(BS);
-  const float nsn = -sn;
-  uint32_t byte = 0;
-#pragma unroll
-  for (int m = 0; m < 8; m++) {
-    // (x0, y0, x1, y1) of pair 8 hl + m: int8 loads + cvt (a float table read per lane as
-    // 8 x dwordx4 made the kernel 30 % slower)
-    const int8_t* p8 = c_pattern + (hl * 8 + m) * 4;
-    const float4 pp = make_float4((float)p8[0], (float)p8[1], (float)p8[2], (float)p8[3]);
-    const int t0 = bcb[sample_offset(rotate_fma(pp.x, pp.y, cs, sn, nsn), BS)];
-    const int t1 = bcb[sample_offset(rotate_fma(pp.z, pp.w, cs, sn, nsn), BS)];
-    byte |= (uint32_t)(t0 < t1) << m;
-  }
-  int outpos = opos;
-  for (int l = 0; l < level; l++) outpos += oc[l];
-  const int64_t o = (int64_t)img * kp_total + outpos;
-  desc[o * 32 + hl] = (uint8_t)byte;
-  if (hl == 0) {
+  __syncthreads();
+
+  // ---- phase B: one keypoint per lane of wave 0
+  if (threadIdx.x < kDescTile && active) {
+    const uint2 mm = s_kp[lane];
+    const float angle = orbx_fast_atan2((float)(int)mm.y, (float)(int)mm.x);
+    const float factorPI = (float)(3.14159265358979323846 / 180.f);
+    float sn, cs;
+    orbx_sincosf(angle * factorPI, &sn, &cs);
+    int outpos = opos;
+    for (int l = 0; l < nlevels - 1; l++) outpos += l < level ? oc[l] : 0;  // a uniform loop
+    s_kp[lane] = make_uint2(__float_as_uint(sn), __float_as_uint(cs));
+    s_out[lane] = outpos;
+    const float lscale = G.scale;
     orbx_keypoint k;
     k.x = level ? (float)(cx) * lscale : (float)cx;
     k.y = level ? (float)(cy) * lscale : (float)cy;
-    k.size = lsize;
+    k.size = G.size;
     k.angle = angle;
     k.response = (float)KeyFmt<K>::score(key);
     k.octave = level;
     k.class_id = -1;
-    kps[o] = k;
+    kps[(int64_t)img * kp_total + outpos] = k;
+  }
+  __syncthreads();
+
+  // ---- phase C: the blurred 37 x 37 patch (rBRIEF samples, radius <= 18) by 16-B pieces from
+  // a 16-B aligned start: lane hl takes piece bp of rows br, br + 8, ..., br + 32 (row 36 at the
+  // most, kept by hl < 20).  A piece past the patch's last one re-reads that one; its first
+  // dword lands in the row's dword 12, which no sample of such a patch reaches.
+  const int br = hl >> 2, bp = hl & 3;
+  auto load_blr = [&](const Geo& g, uint4(&v)[BK]) {
+    const int ab = (g.cx - 18) & ~15, lb = ((g.cx + 18) & ~15) - ab;  // first piece, last offset
+    const uint8_t* p = Bp + (uint32_t)(g.off + (g.cy - 18 + br) * g.pitch + ab + min(16 * bp, lb));
+#pragma unroll
+    for (int k = 0; k < BK - 1; k++) v[k] = *(const uint4*)(p + (uint32_t)(8 * k * g.pitch));
+    v[BK - 1] = *(const uint4*)(p + (uint32_t)((32 + min(br, 4) - br) * g.pitch));
+  };
+  constexpr int BS = 4 * BW;
+  {
+    // (x0, y0, x1, y1) of the lane's pairs 8 hl .. 8 hl + 7 as int8, loaded ahead of the rounds
+    // like the row mask above and converted where used (a float table read per lane as 8 x
+    // dwordx4 made the kernel 30 % slower)
+    uint32_t pat[8];
+    {
+      const uint4* pp = (const uint4*)(c_pattern + hl * 32);
+      const uint4 a = pp[0], b = pp[1];
+      pat[0] = a.x, pat[1] = a.y, pat[2] = a.z, pat[3] = a.w;
+      pat[4] = b.x, pat[5] = b.y, pat[6] = b.z, pat[7] = b.w;
+#pragma unroll
+      for (int m = 0; m < 8; m++) asm volatile("" : "+v"(pat[m]));
+    }
+    Geo g = geo(0);
+    uint4 vb[BK] = {};
+    if (g.act) load_blr(g, vb);
+#pragma unroll 1
+    for (int r = 0; r < NR; r++) {
+      const Geo c = g;
+      if (c.act) {
+        uint32_t* d = s_blr[hw] + br * BW + 4 * bp;
+#pragma unroll
+        for (int k = 0; k < BK; k++)
+          if (k < BK - 1 || hl < 20) d[8 * k * BW] = vb[k].x;
+        if (bp < 3) {
+#pragma unroll
+          for (int k = 0; k < BK; k++)
+            if (k < BK - 1 || hl < 20) {
+              d[8 * k * BW + 1] = vb[k].y;
+              d[8 * k * BW + 2] = vb[k].z;
+              d[8 * k * BW + 3] = vb[k].w;
+            }
+        }
+      }
+      if (r + 1 < NR) {  // the next round's loads fly during this round's samples
+        g = geo(r + 1);
+        if (g.act) load_blr(g, vb);
+      }
+      wave_sync();
+      if (c.act) {
+        const int s = kDescKP * r + hw;
+        const uint2 sc = s_kp[s];
+        const float sn = __uint_as_float(sc.x), cs = __uint_as_float(sc.y);
+        // descriptor on the blurred level: byte hl from pairs 8 hl .. 8 hl + 7, LSB first.
+        // Rotated samples in packed f32 with the reference's fmaf pattern, rounded by the magic
+        // addend; the (row, col) -> byte offset bias is folded into the centre address
+        const uint8_t* bc = (const uint8_t*)s_blr[hw] + 18 * BS + (c.cx - ((c.cx - 18) & ~15));
+        const uint8_t* bcb = bc - sample_bias(BS);
+        const float nsn = -sn;
+        uint32_t byte = 0;
+        // (the pattern is converted here, every round: converted once ahead of the rounds it
+        // would hold 32 registers)
+#pragma unroll
+        for (int m = 0; m < 8; m++) asm volatile("" : "+v"(pat[m]));
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+          const uint32_t w = pat[m];
+          const float4 pp = make_float4((float)(int8_t)w, (float)(int8_t)(w >> 8),
+                                        (float)(int8_t)(w >> 16), (float)(int8_t)(w >> 24));
+          const int t0 = bcb[sample_offset(rotate_fma(pp.x, pp.y, cs, sn, nsn), BS)];
+          const int t1 = bcb[sample_offset(rotate_fma(pp.z, pp.w, cs, sn, nsn), BS)];
+          byte |= (uint32_t)(t0 < t1) << m;
+        }
+        desc[((int64_t)img * kp_total + s_out[s]) * 32 + hl] = (uint8_t)byte;
+      }
+      wave_sync();  // the next round's staging overwrites s_blr[hw]
+    }
   }
 }
 
@@ -2482,7 +2596,8 @@ void enqueue_keyed(orbx_plan* P, int n, Profiler& pr, int st_fcell, int st_oct, 
   KpOffsets ko{};
   for (int l = 0; l < L; l++) ko.off[l] = g.lv[l].kp_off;
   note_kernel<K>("k_describe");
-  hipLaunchKernelGGL(k_describe<K>, dim3((g.kp_total + kDescKP - 1) / kDescKP, n), dim3(32 * kDescKP), 0, P->stream,
+  hipLaunchKernelGGL(k_describe<K>, dim3((g.kp_total + kDescTile - 1) / kDescTile, n),
+                     dim3(32 * kDescKP), 0, P->stream,
                      P->d_pyr, g.pyr_bytes, P->d_blur, P->d_lv, L, ko, okey, P->d_oidx,
                      P->d_ocount, g.kp_total, P->d_kps, P->d_desc, P->d_counts);
   pr.mark(P->stream, st_desc);
